@@ -2,7 +2,12 @@
 
 Contract: `python bench.py --gpus N --steps K --warmup W`: N>1 runs one rank per GPU over RCCL,
 either under the caller's torch.distributed.run or, without one, under a torch.distributed.run
-this script starts as a child process (launch_ranks).  Rank 0 prints ONE JSON line.  Default workload (BASELINE.json
+this script starts as a child process (launch_ranks).  Rank 0 prints ONE JSON line.  A plain run does
+only what the headline needs: set up, K warm-up steps, the timed steps, the result line.  `--full` adds
+the legs that take time of their own after the timed region: the CPU baselines and the env kernel's
+dispatch probe (roofline `dispatch_us`; without it the env roofline rests on the in-kernel stamps
+alone).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+Default workload (BASELINE.json
 configs[2] at 4096 envs per GPU; the metric's config):
 
   --mode ppo (default): one step = one full PPO iteration of clean_pufferl exactly as
@@ -35,7 +40,7 @@ the dispatch and the end-of-kernel release (profiles/r05_clock_vs_rocprof.json).
 (2 x FETCH_SIZE + WRITE_SIZE, gfx950 correction) read from profiles/traffic[_fused]_<envs>.json
 when present, else null.
 
-cpu_baseline: the numpy oracle (oracle/phc_oracle.py) env step on the same 4096-env batch at
+cpu_baseline (--full): the numpy oracle (oracle/phc_oracle.py) env step on the same 4096-env batch at
 1 thread and over all available cores (forked env shards), plus the C restatement of the
 reference's GAE, bounded to ~10 s, rank 0 at N=1 only.  An env-step-only comparison (the PPO
 GEMMs have no CPU oracle); the line says so.
@@ -131,7 +136,13 @@ def parse():
     ap.add_argument("--physics", choices=["replay", "articulated"], default="replay",
                     help="replay = BASELINE configs[1]'s physics stand-in (the headline); articulated = the N3 "
                          "articulated-body step (phc_physics_step) in its place")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline after the timed steps: the CPU baselines "
+                         "(cpu_baseline, cpu_baseline_physics) and the env kernel's dispatch probe (dispatch_us)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; seeded row samples of the large arrays, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--traffic-file", default=None)
     ap.add_argument("--dp-mode", choices=["grouped", "per_layer", "split"], default="grouped",
@@ -447,6 +458,7 @@ class Runner:
                 actions, logprob, _, value = self.policy(o)
             exp.store(o, None, value.flatten(), actions, logprob, r, d, t, env_id, mask, n_valid=a.envs)
             self.env.send(actions)
+            self.last = (actions, logprob, value)
             return a.envs
         g0 = self.info.global_step
         ev = None
@@ -463,7 +475,7 @@ class Runner:
             self.policy.policy.update_amp_obs_rms(self.components.experience.amp_obs)
         if ev:
             ev[2].record()
-        self.cp.train(self.components, self.info, self.util)
+        self.last = self.cp.train(self.components, self.info, self.util)
         if ev:
             ev[3].record()
             self._gpu_phases.append(ev)
@@ -521,6 +533,65 @@ def launch_ranks(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", f"--master-port={port}", os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.run(cmd).returncode
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6  # of all the files of one --dump-outputs together
+DUMP_ROWS = 1024  # rows kept of an array with more (the same seeded row choice for every such array)
+DUMP_PARAMS = 1 << 20  # elements kept of the flattened policy parameters
+
+
+def _sample(n, k):
+    """Sorted indices of a fixed, seeded choice of k of n items (all of them when n <= k)."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+
+def collect_outputs(runner):
+    """name -> float32 array of what the last timed step handed its caller, per mode:
+      env      PHCPufferEnv.step's return: observations, rewards, terminals, truncations
+      rollout  the same + the policy's actions, log-probabilities and values of that step
+      ppo      the iteration's losses (train()'s return, one file per field), the updated policy
+               parameters, the rollout batch the update trained on (obs / actions / logprobs / rewards /
+               dones / values) with its advantages and returns, and the env's buffers after the last step
+    Arrays of more than DUMP_ROWS rows keep a seeded sample of rows, the flattened parameters a seeded
+    sample of DUMP_PARAMS elements: fixed by the shapes alone, so two runs keep the same entries."""
+    torch.cuda.synchronize()
+    env, mode = runner.env, runner.args.mode
+    t = {"env_observations": env.observations, "env_rewards": env.rewards, "env_terminals": env.terminals,
+         "env_truncations": env.truncations}
+    if mode == "rollout":
+        t.update(zip(("actions", "logprobs", "values"), runner.last))
+    if mode == "ppo":
+        import dataclasses
+
+        for k, v in dataclasses.asdict(runner.last).items():
+            t["loss_" + k] = torch.tensor([float(v)])
+        exp = runner.components.experience
+        for k in ("obs", "actions", "logprobs", "rewards", "dones", "values"):
+            t["batch_" + k] = getattr(exp, k)
+        t["batch_advantages"], t["batch_returns"] = exp.b_advantages.reshape(-1), exp.b_returns.reshape(-1)
+        flat = torch.cat([p.detach().reshape(-1).float() for p in runner.policy.parameters()])
+        t["policy_parameters"] = flat[torch.from_numpy(_sample(flat.numel(), DUMP_PARAMS)).to(flat.device)]
+    out = {}
+    for k, v in t.items():
+        v = v.detach()
+        v = v.reshape(v.shape[0], -1) if v.dim() > 1 else v.reshape(-1)
+        if v.dim() > 1 or v.shape[0] > DUMP_PARAMS:
+            v = v[torch.from_numpy(_sample(v.shape[0], DUMP_ROWS)).to(v.device)]
+        out[k] = v.to(torch.float32).cpu().numpy()
+    return out
+
+
+def dump_outputs(directory, runner):
+    """--dump-outputs: write collect_outputs(runner) as DIRECTORY/<name>.npy (float32)."""
+    arrays = collect_outputs(runner)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def main():
@@ -600,9 +671,11 @@ def main():
         env.env.physics.timer = None
         phys_launches = ptimer.count
         phys_s = ptimer.total_ms() * 1e-3 / max(phys_launches, 1)
+    if args.dump_outputs and rank == 0:  # before anything steps the env further
+        dump_outputs(args.dump_outputs, runner)
     # the env kernel's dispatch overhead (for the rocprof-basis roofline), measured on eager launches after
-    # the timed region (replay physics: one launch per step)
-    disp_us = env_dispatch_us(env, runner.actions) if args.physics == "replay" else None
+    # the timed region (replay physics: one launch per step): a run of its own, so --full only
+    disp_us = env_dispatch_us(env, runner.actions) if args.full and args.physics == "replay" else None
     t = torch.tensor([elapsed, kern_s], dtype=torch.float64, device=device)
     counts = [float(processed)]
     if world > 1:
@@ -642,7 +715,7 @@ def main():
             with open(tf) as f:
                 traffic = json.load(f).get("bytes_per_launch")
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.physics == "replay":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.physics == "replay":
             cpu = cpu_baseline(env, packed, args.cpu_seconds)
         workloads = {
             "ppo": "clean_pufferl PPO iteration: evaluate %d rows (PHCPolicy %s inference + PHCPufferEnv.step) + "
@@ -694,7 +767,7 @@ def main():
             out["config"]["dp"] = dp
         if args.physics == "articulated":
             out["roofline_physics"] = physics_roofline(args, phys_s, phys_launches)
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 out["cpu_baseline_physics"] = physics_cpu_baseline(args.cpu_seconds)
         env_roof = {"bound": "hbm",
                     "kernel": "phc_env_step_replay (action->PD + replay physics + env step, one launch: the whole "

@@ -88,6 +88,60 @@ def test_two_rank_gloo_bench_reports_rows_over_wall():
     assert out["value"] == pytest.approx(rows / wall_s, rel=1e-9)
 
 
+def test_plain_run_leaves_the_side_legs_to_full(monkeypatch):
+    """--full is off by default (a plain run times its steps and prints the line); --steps / --warmup
+    are taken as given."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = b.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_sample_is_fixed_by_the_shape():
+    import numpy as np
+
+    b = _bench()
+    assert np.array_equal(b._sample(5, 8), np.arange(5))
+    i, j = b._sample(4096, 1024), b._sample(4096, 1024)
+    assert np.array_equal(i, j) and len(np.unique(i)) == 1024 and np.all(np.diff(i) > 0) and i[-1] < 4096
+
+
+@pytest.mark.gpu
+def test_dump_outputs_env_mode(tmp_path, monkeypatch):
+    """--dump-outputs of an env-mode run: the step's four return arrays as float32 .npy files, the
+    sampled rows equal to those rows of the env's buffers, and the same from a second identical run."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--mode", "env", "--envs", "1500", "--steps", "3", "--warmup", "1"])
+    got = []
+    for run in range(2):
+        args = b.parse()
+        torch.cuda.set_device(0)
+        torch.manual_seed(1234)
+        env, _, cfg = b.build_env(args, 0)
+        runner = b.Runner(args, env, cfg)
+        for _ in range(args.warmup + args.steps):
+            runner.step()
+        d = tmp_path / str(run)
+        b.dump_outputs(str(d), runner)
+        files = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(files) == {"env_observations", "env_rewards", "env_terminals", "env_truncations"}
+        assert all(v.dtype == np.float32 for v in files.values())
+        rows = b._sample(1500, b.DUMP_ROWS)
+        assert files["env_observations"].shape == (b.DUMP_ROWS, env.observations.shape[1])
+        np.testing.assert_array_equal(files["env_observations"], env.observations.cpu().numpy()[rows])
+        np.testing.assert_array_equal(files["env_rewards"], env.rewards.cpu().numpy())
+        assert np.isfinite(files["env_observations"]).all() and np.abs(files["env_observations"]).max() > 0
+        got.append(files)
+    for k in got[0]:
+        np.testing.assert_array_equal(got[0][k], got[1][k])
+
+
 def _dp_worker(rank, world, port, root, out):
     import torch
     import torch.distributed as dist

@@ -13,7 +13,7 @@ for r in $(seq 1 ${ROUNDS:-1}); do
     tag=${v//[+=]/_}
     log="$OUT/bench_${tag}_$r.log"
     env PHC_HIP_LIB=$ROOT/puffer-phc_amd/lib/$so ${settings//+/ } timeout -k 10 300 python bench.py \
-      --steps ${STEPS:-5} --warmup ${WARMUP:-5} --no-cpu-baseline ${BENCH_ARGS:-} > "$log" 2>&1 || { tail -5 "$log"; exit 4; }
+      --full --steps ${STEPS:-5} --warmup ${WARMUP:-5} --no-cpu-baseline ${BENCH_ARGS:-} > "$log" 2>&1 || { tail -5 "$log"; exit 4; }
     python - "$log" "$v" <<'EOF'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@
 #   TAG       output directory under gpurun_out/ (default: pass)
 #   STAGES    any of, in this order:
 #     tests   pytest -m gpu (TESTS= a test path / -k expression list; default: the whole GPU suite)
-#     bench   the driver's command `bench.py --steps 20 --warmup 5`, BENCH_RUNS times (default 2)
+#     bench   `bench.py --full --steps 20 --warmup 5` (CPU baselines and dispatch probe included), BENCH_RUNS times (default 2)
 #     trace   rocprofv3 kernel trace + stats of the PPO iteration; idle gaps and phase split
 #     pmc     FETCH_SIZE / WRITE_SIZE passes (separate) over the trunk GEMMs and the env step
 #     env     bench --mode env at 4096 and 32768 envs, their kernel stats and HBM counters
@@ -35,7 +35,7 @@ if has tests; then
 fi
 if has bench; then
   for r in $(seq 1 "${BENCH_RUNS:-2}"); do
-    timeout -k 10 300 python bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} > "$O/bench_ppo_4096_s20_$r.log" 2>&1 \
+    timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} > "$O/bench_ppo_4096_s20_$r.log" 2>&1 \
       || fail bench "$O/bench_ppo_4096_s20_$r.log"
     tail -1 "$O/bench_ppo_4096_s20_$r.log" | cut -c1-160
   done
@@ -64,7 +64,7 @@ if has pmc; then
 fi
 if has env; then
   for E in 4096 32768; do
-    timeout -k 10 300 python bench.py --mode env --envs $E --no-cpu-baseline > "$O/bench_env_$E.log" 2>&1 || fail env "$O/bench_env_$E.log"
+    timeout -k 10 300 python bench.py --full --mode env --envs $E --no-cpu-baseline > "$O/bench_env_$E.log" 2>&1 || fail env "$O/bench_env_$E.log"
     tail -1 "$O/bench_env_$E.log" | cut -c1-140
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/trace_env_$E" -o run --output-format csv -- \
       python3 "$ROOT/bench.py" --mode env --envs $E --no-cpu-baseline > "$O/trace_env_$E.log" 2>&1 || fail envtrace "$O/trace_env_$E.log"
