@@ -385,6 +385,13 @@ size_t phc_twin_gemm_workspace_bytes(int64_t m, int32_t batch, int32_t n);
  * bias_grad set they are summed into it by a second launch. */
 int64_t phc_twin_gemm_m_tiles(int64_t m, int32_t n, int32_t batch);
 int phc_twin_gemm(const phc_gemm_desc *desc, float *bias_grad, void *workspace, void *stream);
+/* What phc_twin_gemm would launch for this descriptor (no launch; the same code decides both):
+ * bits 0-31 the grid size in workgroups, bits 32-47 the tile edge (128 or 256: square tiles), bit 48
+ * set when the launch is a persistent grid of wave-specialised workgroups (forward epilogues, and
+ * DSILU_GRAD on whole 256 x 256 tiles with a 16-byte aligned half-precision aux and a half-precision
+ * output).  -1, with phc_last_error set, for a descriptor phc_twin_gemm rejects by its shape, types,
+ * epilogue, twin geometry, a missing bias / aux or max_workgroups; a, b and out are not looked at. */
+int64_t phc_twin_gemm_plan(const phc_gemm_desc *desc);
 
 /* R21: the twin trunks' weight gradients (the reference's autograd of nn.Linear,
  * policies/phc_policy.py:10-38 under clean_pufferl/core.py:354 loss.backward()).  For b < batch

@@ -257,6 +257,7 @@ _EXPORTS = {
     "phc_twin_gemm_workspace_bytes": (ctypes.c_size_t, [c_i64, ctypes.c_int32, ctypes.c_int32]),
     "phc_twin_gemm": (ctypes.c_int, [ctypes.POINTER(GemmDescC), c_vp, c_vp, c_vp]),
     "phc_twin_gemm_m_tiles": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "phc_twin_gemm_plan": (ctypes.c_int64, [ctypes.POINTER(GemmDescC)]),
     "phc_weight_grad": (ctypes.c_int, [ctypes.POINTER(WgradDescC), c_vp]),
     "phc_weight_grad_group": (ctypes.c_int, [ctypes.POINTER(WgradProblemC), ctypes.c_int32, c_i64, ctypes.c_int32,
                                               ctypes.c_int32, c_vp]),
@@ -660,20 +661,12 @@ def twin_gemm_m_tiles(m, n, batch):
 GEMM_LAUNCHES = [0]
 
 
-def twin_gemm(a, b, epilogue, out, twin, bias=None, aux=None, aux_layout=GROUPED, out_layout=GROUPED,
-              bias_grad=None, max_workgroups=0, bias_partial=None, k_valid=0):
-    """out = epilogue(a[b] @ b[b]^T) for a [batch?, m, k], b [batch?, n, k] (phc_twin_gemm).
-    twin = (groups, cols) of the output / aux tensors' logical columns.  max_workgroups > 0:
-    a persistent grid of that many workgroups looping over the tiles.  Grad epilogues: bias_grad
-    [batch * n] receives the column sums; or bias_partial, fp32 [twin_gemm_m_tiles(m, n, batch),
-    batch * n], the per-m-tile column sums for the caller to reduce (no second launch).  k_valid: the
-    algorithmic depth when a's / b's last columns are zero padding (the kernel timer's FLOP count only)."""
+def _gemm_desc(a, b, epilogue, out, twin, bias, aux, aux_layout, out_layout, max_workgroups, k_valid):
+    """The phc_gemm_desc of a twin_gemm call (arguments validated) and its m, n, batch."""
     pa, abs_, lda, ba, m, k = _operand(a, "a")
     pb, bbs, ldb, bb, n, kb = _operand(b, "b")
     if kb != k or (ba != bb and ba != 1 and bb != 1):
         raise ValueError(f"twin_gemm: operand shapes {tuple(a.shape)} x {tuple(b.shape)}^T do not match")
-    if m > 4096:
-        GEMM_LAUNCHES[0] += 1
     if a.dtype != b.dtype:
         raise ValueError("twin_gemm: operands must share a dtype")
     batch = max(ba, bb)
@@ -687,6 +680,32 @@ def twin_gemm(a, b, epilogue, out, twin, bias=None, aux=None, aux_layout=GROUPED
                   _ptr(bias, torch.float32, (batch * n,), "bias", nullable=True),
                   aux.data_ptr() if aux is not None else None, out.data_ptr(), aux_layout, out_layout, G, C,
                   DTYPE_CODE[aux.dtype] if aux is not None else 0, int(max_workgroups), int(k_valid))
+    return d, m, n, batch
+
+
+def twin_gemm_plan(a, b, epilogue, out, twin, bias=None, aux=None, aux_layout=GROUPED, out_layout=GROUPED,
+                   bias_grad=None, max_workgroups=0, bias_partial=None, k_valid=0):
+    """What twin_gemm would launch for the same arguments (phc_twin_gemm_plan; nothing runs): a dict of
+    tile (edge of the square tiles), grid (workgroups) and wave_specialised (the persistent grid of
+    wave-specialised workgroups).  bias_grad / bias_partial do not bear on the choice."""
+    d = _gemm_desc(a, b, epilogue, out, twin, bias, aux, aux_layout, out_layout, max_workgroups, k_valid)[0]
+    v = int(lib().phc_twin_gemm_plan(ctypes.byref(d)))
+    if v < 0:
+        raise ValueError("twin_gemm_plan: " + lib().phc_last_error().decode())
+    return {"grid": v & 0xFFFFFFFF, "tile": (v >> 32) & 0xFFFF, "wave_specialised": bool((v >> 48) & 1)}
+
+
+def twin_gemm(a, b, epilogue, out, twin, bias=None, aux=None, aux_layout=GROUPED, out_layout=GROUPED,
+              bias_grad=None, max_workgroups=0, bias_partial=None, k_valid=0):
+    """out = epilogue(a[b] @ b[b]^T) for a [batch?, m, k], b [batch?, n, k] (phc_twin_gemm).
+    twin = (groups, cols) of the output / aux tensors' logical columns.  max_workgroups > 0:
+    a persistent grid of that many workgroups looping over the tiles.  Grad epilogues: bias_grad
+    [batch * n] receives the column sums; or bias_partial, fp32 [twin_gemm_m_tiles(m, n, batch),
+    batch * n], the per-m-tile column sums for the caller to reduce (no second launch).  k_valid: the
+    algorithmic depth when a's / b's last columns are zero padding (the kernel timer's FLOP count only)."""
+    d, m, n, batch = _gemm_desc(a, b, epilogue, out, twin, bias, aux, aux_layout, out_layout, max_workgroups, k_valid)
+    if m > 4096:
+        GEMM_LAUNCHES[0] += 1
     ws = None
     if bias_grad is not None:
         _ptr(bias_grad, torch.float32, (batch * n,), "bias_grad")

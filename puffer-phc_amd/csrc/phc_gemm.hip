@@ -660,6 +660,14 @@ constexpr bool kWsTile = PHC_GEMM_WS && TL::BM == 256 && TL::BN == 256 && TL::kW
                          PHC_GEMM_DEFER && !PHC_GEMM_8PH &&
                          !(epi_base(EPI) == PHC_EPI_SILU_GRAD || EPI == PHC_EPI_RELU_GRAD);
 
+// the silu'-aux input gradient (DSILU_GRAD) has wave-specialised role copies too, for whole tiles with
+// a half-precision aux and output (the staged-aux epilogue below): a separate kernel, chosen at
+// launch (gemm_plan), beside the generic persistent copy that keeps ragged tiles and an fp32 aux
+template <int EPI, typename TL, typename OutT>
+constexpr bool kWsGrad = PHC_GEMM_WS && EPI == PHC_EPI_DSILU_GRAD && TL::BM == 256 && TL::BN == 256 && TL::kWaves == 8 &&
+                         TL::STAGES == 2 && TL::BK == 64 && PHC_GEMM_DEFER && !PHC_GEMM_8PH && sizeof(OutT) == 2 &&
+                         PHC_GEMM_EPI_VW == 8;
+
 constexpr int kWsBiasBytes = 1024;  // 256 fp32 bias values
 
 template <int EPI, typename TL, typename OutT> struct EpStage {
@@ -679,6 +687,11 @@ template <int EPI, typename TL, typename OutT> struct EpStage {
 // writes, image reads + global stores).  Separate instantiations, so the compiler's wait insertion
 // for each role sees only its own memory operations (in one shared body it put vmcnt(0) waits meant
 // for the DMA into the store waves' path as well).
+// The DSILU_GRAD role copies (kWsGrad; whole tiles, half-precision aux, checked at launch): the DMA
+// waves also issue the aux LDS-DMA (8 per wave and pass) and own its vmcnt waits; the store waves
+// read image and aux slot from LDS, 8 image rows per thread and pass, and carry the column sums in
+// two accumulators (even / odd row of the thread = row groups rg / rg + 8 of the 512-thread
+// epilogue), so the bias-gradient partials add up in the one-tile kernel's order, bit for bit.
 template <typename T, typename OutT, int EPIX, typename TL, int ROLE = 0>
 __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, int wg) {
   constexpr int EPI = epi_base(EPIX);
@@ -693,9 +706,10 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
   asm volatile("" : "+v"(tid_));
   const int tid = tid_, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / TL::WGN, wn = wave % TL::WGN;
+  constexpr bool kWsG = WS && kGrad;  // the DSILU_GRAD role copies
   static_assert(!WS || (TL::kWaves == 8 && TL::STAGES == 2 && PHC_GEMM_DEFER && !PHC_GEMM_8PH &&
-                        !(EPI == PHC_EPI_SILU_GRAD || EPI == PHC_EPI_RELU_GRAD)),
-                "wave specialisation: 8-wave, 2-stage deferred main loop, store-only epilogues");
+                        (!kGrad || kWsGrad<EPIX, TL, OutT>)),
+                "wave specialisation: 8-wave, 2-stage deferred main loop, store-only epilogues or DSILU_GRAD");
   const int wsg = __builtin_amdgcn_readfirstlane(wave);  // wave-uniform (SGPR)
   constexpr bool dma_wave = ROLE != 2;
   constexpr int kDW = WS ? TL::kWaves / 2 : TL::kWaves;  // waves issuing the operand DMA
@@ -709,22 +723,37 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
   using ES = EpStage<EPI, TL, OutT>;
   constexpr int EP = ES::kPasses, WR = TL::TM / EP;
   const int kt_last = (g.k / TL::BK - 1) & 1;  // the operand buffer the last K-step reads
-  const bool stage_aux = ES::kOn && g.aux_half && g.tc % BN == 0 && g.n % BN == 0 && m0 + BM <= g.m;
+  // the role copies run staged whole tiles only (the launch checks what this tests per tile)
+  const bool stage_aux = kWsG || (ES::kOn && g.aux_half && g.tc % BN == 0 && g.n % BN == 0 && m0 + BM <= g.m);
   // aux slot s: the halves of the buffer the last K-step does not read, then the spare 32 KB
   auto aux_slot = [&](int sl) -> char * {
     return sl < 2 ? smem + (kt_last ^ 1) * TL::kStageBytes + sl * ES::kSlotBytes : smem + TL::kOpBytes;
   };
   // LDS-DMA of pass p's 64 aux rows (512 B each, image-row order) into a slot: wave-instruction i
-  // moves rows 2i, 2i + 1; 4 per wave
+  // moves rows 2i, 2i + 1; 4 per wave, or 8 per DMA wave in the role copies (none in the store role)
   auto stage_aux_pass = [&](int p, char *slot) {
-    if constexpr (ES::kOn) {
+    if constexpr (ES::kOn && ROLE != 2) {
       const int64_t lc0 = (int64_t)bt * g.n + n0;
       const bool split = g.aux_layout == PHC_LAYOUT_SPLIT;
       const int64_t base0 = split ? lc0 : (lc0 / g.tc) * g.m * g.tc + lc0 % g.tc;
       const int64_t stride = split ? (int64_t)g.tg * g.tc : g.tc;
+      constexpr int kPerWave = 32 / kDW;
+      if constexpr (WS) {
+        // DMA wave w moves image rows 16 w .. 16 w + 15: a wave-uniform source (scalar registers) plus
+        // one 32-bit per-lane byte offset for all of its instructions (per-instruction 64-bit lane
+        // addresses, hoisted above the main loop, spilled)
+        const unsigned lane_off = (unsigned)(((lane >> 5) * stride + (lane & 31) * 8) * 2);
+        const int64_t row0 = m0 + (wsg >> 1) * TL::TM + p * WR + (wsg & 1) * 16;
+        const char *ub = reinterpret_cast<const char *>(static_cast<const T *>(g.aux) + base0 + row0 * stride);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = wave * 4 + u;
+        for (int u = 0; u < kPerWave; ++u)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(ub + (int64_t)u * (2 * stride * 2) + lane_off),
+                                           (lds_void *)(slot + (wsg * kPerWave + u) * 1024), 16, 0, 0);
+        return;
+      }
+#pragma unroll
+      for (int u = 0; u < kPerWave; ++u) {
+        const int i = wave * kPerWave + u;
         const int rr = 2 * i + (lane >> 5);
         const int64_t tr = m0 + (rr / WR) * TL::TM + p * WR + rr % WR;
         const T *src = static_cast<const T *>(g.aux) + base0 + tr * stride + (lane & 31) * 8;
@@ -746,7 +775,7 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
   const int n0_ = n0;
   // WS: whole tiles stage through per-lane pointers (stage_tile_ws); ragged ones (never in the PPO
   // minibatch) through the clamped generic path
-  const bool ws_full = WS && m0 + BM <= g.m && n0 + BN <= g.n;
+  const bool ws_full = kWsG || (WS && m0 + BM <= g.m && n0 + BN <= g.n);
   const WsSrc ws_a = ws_src(A, g.lda, m0, wsg, lane), ws_b = ws_src(B, g.ldb, n0, wsg, lane);
   if constexpr (ROLE == 1) {
     if (g.bias && (EPI == PHC_EPI_BIAS || EPI == PHC_EPI_BIAS_SILU || EPI == PHC_EPI_BIAS_RELU)) {
@@ -858,7 +887,11 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
     for (int i = 0; i < MI; ++i)
 #pragma unroll
       for (int j = 0; j < NI; ++j) t += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    if (t == 1234.5f) static_cast<float *>(g.out)[0] = t;
+    if constexpr (kWsG && ROLE == 1) {  // no store in the DMA role; its aux DMA of the last K-step lands
+      asm volatile("s_waitcnt vmcnt(0)" ::"v"(t) : "memory");
+    } else {
+      if (t == 1234.5f) static_cast<float *>(g.out)[0] = t;
+    }
     return;
   }
   // ---- epilogue.  The accumulators (lane: column lane & 15, rows 4 * (lane >> 4) + e of each
@@ -882,12 +915,13 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
   const int cv = (st_tid % kColThreads) * VW, rg = st_tid / kColThreads;
   const int gcol = n0 + cv;
   const bool vec = gcol + VW - 1 < g.n && g.tc % VW == 0;
-  const bool full = vec && m0 + BM <= g.m;
-  float biasv[VW], csum[VW];
+  const bool full = kWsG || (vec && m0 + BM <= g.m);
+  float biasv[VW], csum[VW], csum_odd[kWsG ? VW : 1];  // csum_odd: the role copies' odd rows (row group rg + 8)
 #pragma unroll
   for (int q = 0; q < VW; ++q) {
     biasv[q] = 0.0f;
     csum[q] = 0.0f;
+    if constexpr (kWsG) csum_odd[q] = 0.0f;
   }
   if constexpr (ROLE == 2) {
     if (EPI != PHC_EPI_STORE && g.bias) {
@@ -932,7 +966,7 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
   const bool pipe = kGrad && g.aux_half;
   RawV raw[2][kGrad ? U : 1];
   auto load_raw = [&](int pass, int b) {
-    if constexpr (kGrad) {
+    if constexpr (kGrad && !kWsG) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t row = m0 + trow(pass, b * U + u);
@@ -957,7 +991,14 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
           const int c = wn * TL::TN + j * 16 + (lane & 15);
           ep[r * BN + (c ^ (((r >> 2) & 3) << 4))] = acc[i][j][e];
         }
-    if (stage_aux) {
+    if constexpr (kWsG) {
+      // the DMA role owns the waits: it issues no store, so the aux DMA is all its vmcnt holds (passes
+      // 0-2 from the last K-step before pass 0, pass 3's from pass 1 before pass 3).  The store role
+      // reads a slot only past the barrier below, which follows these waits: it waits for nothing
+      if constexpr (ROLE == 1) {
+        if (pass == 0 || pass == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+    } else if (stage_aux) {
       // this wave's aux DMA for the pass has landed (all waves' after the barrier): passes 0-2 were
       // issued in the last K-step; pass 3's in pass 1, before the 2 x IT stores of passes 1 and 2
       if (pass == 0 || g.discard) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1014,7 +1055,12 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
 #pragma unroll
               for (int q = 0; q < VW; ++q) {
                 v[q] = v[q] * av[u][q];
-                csum[q] += v[q];
+                if constexpr (kWsG) {
+                  if ((i0 + u) & 1) csum_odd[q] += v[q];
+                  else csum[q] += v[q];
+                } else {
+                  csum[q] += v[q];
+                }
               }
             } else {
 #pragma unroll
@@ -1051,6 +1097,12 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
             }
           }
           if (g.discard != 2) gemm_store_v<OutT, VW>(g.out, ob + row * os, v, g.nt & 1);
+        }
+        if constexpr (kWsG) {
+          // the sums are taken here: left free, the additions sank below the last pass (they are needed
+          // only under g.partial) and every product of the tile stayed live until then, in scratch
+#pragma unroll
+          for (int q = 0; q < VW; ++q) asm volatile("" : "+v"(csum[q]), "+v"(csum_odd[q]));
         }
       }
       continue;
@@ -1117,6 +1169,46 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
   }
   if constexpr (kGrad) {
     if (!g.partial) return;
+    if constexpr (kWsG) {
+      // store wave v holds, after the shuffle, what waves v (csum: row groups 2v, 2v + 1) and v + 4
+      // (csum_odd: row groups 2v + 8, 2v + 9) of the 512-thread epilogue write to slots v and v + 4;
+      // the 8-slot sum below then adds in that epilogue's order.  The DMA role only keeps the barriers
+      if constexpr (ROLE == 2) {
+#pragma unroll
+        for (int q = 0; q < VW; ++q) {
+          csum[q] += __shfl_xor(csum[q], 32, 64);
+          csum_odd[q] += __shfl_xor(csum_odd[q], 32, 64);
+        }
+      }
+      lds_barrier();  // the epilogue image is no longer read
+      if constexpr (ROLE == 2) {
+        if (lane < kColThreads) {
+          const int v = wsg - TL::kWaves / 2;
+#pragma unroll
+          for (int h = 0; h < VW / 4; ++h) {
+            *reinterpret_cast<float4 *>(&ep[v * BN + lane * VW + 4 * h]) =
+                float4{csum[4 * h], csum[4 * h + 1], csum[4 * h + 2], csum[4 * h + 3]};
+            *reinterpret_cast<float4 *>(&ep[(v + 4) * BN + lane * VW + 4 * h]) =
+                float4{csum_odd[4 * h], csum_odd[4 * h + 1], csum_odd[4 * h + 2], csum_odd[4 * h + 3]};
+          }
+        }
+      }
+      lds_barrier();
+      if constexpr (ROLE == 2) {
+        if (st_tid < kColThreads) {
+          float o[VW];
+#pragma unroll
+          for (int q = 0; q < VW; ++q) o[q] = 0.0f;
+          for (int w = 0; w < TL::kWaves; ++w)
+#pragma unroll
+            for (int q = 0; q < VW; ++q) o[q] += ep[w * BN + cv + q];
+          float *pr = g.partial + (int64_t)tm * (g.batch * g.n) + bt * g.n;
+#pragma unroll
+          for (int q = 0; q < VW; ++q) pr[gcol + q] = o[q];
+        }
+      }
+      return;
+    }
     // column sums over the tile's rows: row groups inside a wave by shuffle, the waves by LDS
     if constexpr (kColThreads < 64) {
 #pragma unroll
@@ -1154,14 +1246,16 @@ __device__ __forceinline__ void twin_gemm_tile(const GemmArgs &g, char *smem, in
 // [s * nwg, (s + 1) * nwg) out XCD-major, so the workgroups sharing an XCD's L2 walk neighbouring
 // tiles of the same A panels at every step.  Separate instantiations: inlined into one kernel the
 // persistent copy's hoisted epilogue addresses spilled registers of the one-tile copy as well.
-template <typename T, typename OutT, int EPI, typename TL, bool PERSIST>
+// WSG: the persistent loop in DSILU_GRAD's role copies (kWsGrad), launched for eligible shapes only.
+template <typename T, typename OutT, int EPI, typename TL, bool PERSIST, bool WSG = false>
 __global__ __launch_bounds__(TL::kThreads) __attribute__((amdgpu_waves_per_eu(TL::kWavesPerEU, 8))) void k_twin_gemm(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [stage][A BM rows | B BN rows]
   const int nwg = gridDim.x, orig = blockIdx.x;
   launch_clock_begin(g.clk);
   if constexpr (!PERSIST) {
     twin_gemm_tile<T, OutT, EPI, TL>(g, smem, xcd_first(nwg, orig % 8) + orig / 8);
-  } else if constexpr (kWsTile<EPI, TL>) {
+  } else if constexpr (kWsTile<EPI, TL> || WSG) {
+    static_assert(!WSG || kWsGrad<EPI, TL, OutT>, "role copies of the grad epilogue: DSILU_GRAD, 256 x 256, half-precision out");
     // the same tile sequence in both role copies: their barriers pair up one for one
     const int total = g.tiles_m * g.tiles_n * g.batch;
     const int x = orig % 8, l = orig / 8;
@@ -1501,47 +1595,53 @@ static phc_kernel_timer *g_gemm_timer = nullptr;  // bench.py measurement aid (p
 constexpr int64_t kTimedMinRows = 4096;
 
 template <typename T, typename OutT, int EPI, typename TL>
-static void launch_one(const GemmArgs &g, int64_t blocks, hipStream_t st) {
+static void launch_one(const GemmArgs &g, int64_t blocks, bool ws_grad, hipStream_t st) {
   const bool persist = blocks < (int64_t)g.tiles_m * g.tiles_n * g.batch;
   auto kernel = persist ? k_twin_gemm<T, OutT, EPI, TL, true> : k_twin_gemm<T, OutT, EPI, TL, false>;
   constexpr int lds = EpStage<EPI, TL, OutT>::kLdsBytes;
   static bool attr = [&] {
     for (auto k : {k_twin_gemm<T, OutT, EPI, TL, true>, k_twin_gemm<T, OutT, EPI, TL, false>})
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if constexpr (kWsGrad<EPI, TL, OutT>)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_twin_gemm<T, OutT, EPI, TL, true, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     return true;
   }();
   (void)attr;
+  if constexpr (kWsGrad<EPI, TL, OutT>) {
+    if (persist && ws_grad) kernel = k_twin_gemm<T, OutT, EPI, TL, true, true>;
+  }
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(TL::kThreads), lds, st, g);
 }
 
 template <typename T, typename OutT, int EPI>
-static void launch_cfg(int cfg, const GemmArgs &g, int64_t blocks, hipStream_t st) {
-  if (cfg == kCfg256sq) launch_one<T, OutT, EPI, Tile256tw>(g, blocks, st);
-  else launch_one<T, OutT, EPI, Tile128x2>(g, blocks, st);
+static void launch_cfg(int cfg, const GemmArgs &g, int64_t blocks, bool ws_grad, hipStream_t st) {
+  if (cfg == kCfg256sq) launch_one<T, OutT, EPI, Tile256tw>(g, blocks, ws_grad, st);
+  else launch_one<T, OutT, EPI, Tile128x2>(g, blocks, ws_grad, st);
 }
 
 template <typename T, typename OutT>
-static void launch_epi(int epi, int cfg, const GemmArgs &g, int64_t blocks, hipStream_t st) {
+static void launch_epi(int epi, int cfg, const GemmArgs &g, int64_t blocks, bool ws_grad, hipStream_t st) {
   switch (epi) {
-    case PHC_EPI_STORE: launch_cfg<T, OutT, PHC_EPI_STORE>(cfg, g, blocks, st); break;
-    case PHC_EPI_BIAS: launch_cfg<T, OutT, PHC_EPI_BIAS>(cfg, g, blocks, st); break;
-    case PHC_EPI_BIAS_SILU: launch_cfg<T, OutT, PHC_EPI_BIAS_SILU>(cfg, g, blocks, st); break;
-    case PHC_EPI_SILU_GRAD: launch_cfg<T, OutT, PHC_EPI_SILU_GRAD>(cfg, g, blocks, st); break;
-    case PHC_EPI_BIAS_RELU: launch_cfg<T, OutT, PHC_EPI_BIAS_RELU>(cfg, g, blocks, st); break;
-    case PHC_EPI_BIAS_SILU_D: launch_cfg<T, OutT, PHC_EPI_BIAS_SILU_D>(cfg, g, blocks, st); break;
-    case PHC_EPI_DSILU_GRAD: launch_cfg<T, OutT, PHC_EPI_DSILU_GRAD>(cfg, g, blocks, st); break;
-    default: launch_cfg<T, OutT, PHC_EPI_RELU_GRAD>(cfg, g, blocks, st); break;
+    case PHC_EPI_STORE: launch_cfg<T, OutT, PHC_EPI_STORE>(cfg, g, blocks, ws_grad, st); break;
+    case PHC_EPI_BIAS: launch_cfg<T, OutT, PHC_EPI_BIAS>(cfg, g, blocks, ws_grad, st); break;
+    case PHC_EPI_BIAS_SILU: launch_cfg<T, OutT, PHC_EPI_BIAS_SILU>(cfg, g, blocks, ws_grad, st); break;
+    case PHC_EPI_SILU_GRAD: launch_cfg<T, OutT, PHC_EPI_SILU_GRAD>(cfg, g, blocks, ws_grad, st); break;
+    case PHC_EPI_BIAS_RELU: launch_cfg<T, OutT, PHC_EPI_BIAS_RELU>(cfg, g, blocks, ws_grad, st); break;
+    case PHC_EPI_BIAS_SILU_D: launch_cfg<T, OutT, PHC_EPI_BIAS_SILU_D>(cfg, g, blocks, ws_grad, st); break;
+    case PHC_EPI_DSILU_GRAD: launch_cfg<T, OutT, PHC_EPI_DSILU_GRAD>(cfg, g, blocks, ws_grad, st); break;
+    default: launch_cfg<T, OutT, PHC_EPI_RELU_GRAD>(cfg, g, blocks, ws_grad, st); break;
   }
 }
 
-static void launch_gemm(int dtype, int out_dtype, int epi, int cfg, const GemmArgs &g, int64_t blocks,
+static void launch_gemm(int dtype, int out_dtype, int epi, int cfg, const GemmArgs &g, int64_t blocks, bool ws_grad,
                         hipStream_t st) {
   if (dtype == PHC_DT_F16) {
-    if (out_dtype == PHC_DT_F32) launch_epi<_Float16, float>(epi, cfg, g, blocks, st);
-    else launch_epi<_Float16, _Float16>(epi, cfg, g, blocks, st);
+    if (out_dtype == PHC_DT_F32) launch_epi<_Float16, float>(epi, cfg, g, blocks, ws_grad, st);
+    else launch_epi<_Float16, _Float16>(epi, cfg, g, blocks, ws_grad, st);
   } else {
-    if (out_dtype == PHC_DT_F32) launch_epi<__bf16, float>(epi, cfg, g, blocks, st);
-    else launch_epi<__bf16, __bf16>(epi, cfg, g, blocks, st);
+    if (out_dtype == PHC_DT_F32) launch_epi<__bf16, float>(epi, cfg, g, blocks, ws_grad, st);
+    else launch_epi<__bf16, __bf16>(epi, cfg, g, blocks, ws_grad, st);
   }
 }
 
@@ -1589,15 +1689,60 @@ extern "C" int64_t phc_twin_gemm_m_tiles(int64_t m, int32_t n, int32_t batch) {
   return (m + bm - 1) / bm;
 }
 
-extern "C" int phc_twin_gemm(const phc_gemm_desc *d, float *bias_grad, void *workspace, void *stream) {
+// What a launch of this descriptor runs: tile configuration, grid, and whether the persistent loop is
+// the wave-specialised one (phc_twin_gemm launches from this; phc_twin_gemm_plan reports it).
+struct GemmPlan {
+  int cfg;
+  int64_t tiles_m, tiles_n, tiles, blocks;  // tiles: all of them; blocks: the grid
+  bool ws;  // the wave-specialised persistent kernel
+};
+
+static GemmPlan gemm_plan(const phc_gemm_desc *d) {
+  GemmPlan p{};
+  p.cfg = gemm_config(d->m, d->n, d->batch);
+  int bm, bn;
+  gemm_tile_dims(p.cfg, &bm, &bn);
+  p.tiles_m = (d->m + bm - 1) / bm;
+  p.tiles_n = (d->n + bn - 1) / bn;
+  p.tiles = p.tiles_m * p.tiles_n * d->batch;
+  const int64_t tiles = p.tiles;
+  p.blocks = tiles;
+  if (d->max_workgroups > 0 && d->max_workgroups < p.blocks) p.blocks = d->max_workgroups;
+  // 256 x 256 tiles with more tiles than CUs: one persistent workgroup per CU, wave-specialised, so
+  // each tile's epilogue stores drain under the next tile's main loop.  The forward (store-only)
+  // epilogues take any shape (kWsTile); the silu'-aux input gradient (kWsGrad) whole tiles with a
+  // half-precision aux and output, and any other grad launch stays one tile per workgroup (or, under
+  // an explicit max_workgroups, in the generic persistent loop).  PHC_GEMM_WS_GRID=0 keeps one tile
+  // per workgroup (A/B aid).
+  static const bool ws_grid = [] {
+    const char *e = getenv("PHC_GEMM_WS_GRID");
+    return PHC_GEMM_WS && !(e && atoi(e) == 0);
+  }();
+  static const int cus = [] {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+  }();
+  const int epi = epi_base(d->epilogue);
+  const bool grad_epi = epi == PHC_EPI_SILU_GRAD || epi == PHC_EPI_RELU_GRAD;
+  const bool ws_fwd = kWsTile<PHC_EPI_STORE, Tile256tw> && p.cfg == kCfg256sq && !grad_epi;
+  const bool ws_grad = kWsGrad<PHC_EPI_DSILU_GRAD, Tile256tw, _Float16> && p.cfg == kCfg256sq &&
+                       d->epilogue == PHC_EPI_DSILU_GRAD && d->aux_dtype == d->dtype && d->out_dtype == d->dtype &&
+                       d->m % 256 == 0 && d->n % 256 == 0 && d->twin_cols % 256 == 0 &&
+                       (reinterpret_cast<uintptr_t>(d->aux) & 15) == 0;  // the aux rows move as 16-B LDS-DMA
+  if (ws_grid && d->max_workgroups == 0 && (ws_fwd || ws_grad) && p.blocks > cus) p.blocks = cus;
+  p.ws = (ws_fwd || ws_grad) && p.blocks < tiles;
+  return p;
+}
+
+// The descriptor checks of a launch that need neither the operands' addresses nor the bias-gradient
+// arguments: phc_twin_gemm and phc_twin_gemm_plan reject the same descriptors by them.
+static int gemm_desc_check(const phc_gemm_desc *d) {
   PHC_REQUIRE(d, "twin_gemm: null descriptor");
-  PHC_REQUIRE(d->a && d->b && d->out, "twin_gemm: null operand");
   PHC_REQUIRE(d->m > 0 && d->n > 0 && d->k > 0 && d->batch >= 1, "twin_gemm: bad shape");
   PHC_REQUIRE(d->k % kGBK == 0, "twin_gemm: k (%d) must be a multiple of %d (zero-pad the operands)", d->k, kGBK);
   PHC_REQUIRE(d->lda >= d->k && d->ldb >= d->k && d->lda % 8 == 0 && d->ldb % 8 == 0,
               "twin_gemm: leading dimensions must cover k and be multiples of 8");
-  PHC_REQUIRE((reinterpret_cast<uintptr_t>(d->a) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->b) & 15) == 0,
-              "twin_gemm: operands must be 16-byte aligned");
   PHC_REQUIRE(d->dtype == PHC_DT_F16 || d->dtype == PHC_DT_BF16, "twin_gemm: operands must be f16 or bf16");
   PHC_REQUIRE(d->out_dtype == PHC_DT_F32 || d->out_dtype == d->dtype, "twin_gemm: out must be f32 or the operand type");
   PHC_REQUIRE(d->epilogue >= PHC_EPI_STORE && d->epilogue <= PHC_EPI_DSILU_GRAD, "twin_gemm: bad epilogue");
@@ -1611,32 +1756,33 @@ extern "C" int phc_twin_gemm(const phc_gemm_desc *d, float *bias_grad, void *wor
               "twin_gemm: epilogue needs the bias");
   PHC_REQUIRE(!grad_epi || d->aux, "twin_gemm: SILU_GRAD / RELU_GRAD need the (pre-)activation (aux)");
   PHC_REQUIRE(d->aux_dtype == PHC_DT_F32 || d->aux_dtype == d->dtype, "twin_gemm: aux must be f32 or the operand type");
+  PHC_REQUIRE(d->max_workgroups >= 0, "twin_gemm: max_workgroups must be >= 0");
+  PHC_REQUIRE(gemm_plan(d).tiles < (1ll << 31), "twin_gemm: grid too large");
+  return 0;
+}
+
+extern "C" int64_t phc_twin_gemm_plan(const phc_gemm_desc *d) {
+  if (gemm_desc_check(d) != 0) return -1;
+  const GemmPlan p = gemm_plan(d);
+  int bm, bn;
+  gemm_tile_dims(p.cfg, &bm, &bn);
+  return p.blocks | ((int64_t)bm << 32) | ((int64_t)(p.ws ? 1 : 0) << 48);
+}
+
+extern "C" int phc_twin_gemm(const phc_gemm_desc *d, float *bias_grad, void *workspace, void *stream) {
+  if (const int rc = gemm_desc_check(d)) return rc;
+  PHC_REQUIRE(d->a && d->b && d->out, "twin_gemm: null operand");
+  PHC_REQUIRE((reinterpret_cast<uintptr_t>(d->a) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->b) & 15) == 0,
+              "twin_gemm: operands must be 16-byte aligned");
+  const int epi = epi_base(d->epilogue);
+  const bool grad_epi = epi == PHC_EPI_SILU_GRAD || epi == PHC_EPI_RELU_GRAD;
   PHC_REQUIRE(!bias_grad || (grad_epi && workspace),
               "twin_gemm: bias_grad needs the SILU_GRAD / RELU_GRAD epilogue and a workspace");
   PHC_REQUIRE(!workspace || grad_epi, "twin_gemm: a workspace receives the grad epilogues' bias-gradient partials");
   hipStream_t st = as_stream(stream);
-  const int cfg = gemm_config(d->m, d->n, d->batch);
-  int bm, bn;
-  gemm_tile_dims(cfg, &bm, &bn);
-  const int64_t tiles_m = (d->m + bm - 1) / bm;
-  const int64_t tiles_n = (d->n + bn - 1) / bn;
-  int64_t blocks = tiles_m * tiles_n * d->batch;
-  PHC_REQUIRE(blocks < (1ll << 31), "twin_gemm: grid too large");
-  PHC_REQUIRE(d->max_workgroups >= 0, "twin_gemm: max_workgroups must be >= 0");
-  if (d->max_workgroups > 0 && d->max_workgroups < blocks) blocks = d->max_workgroups;
-  // forward (store-only) epilogues on 256 x 256 tiles with more tiles than CUs: one persistent
-  // workgroup per CU, wave-specialised (kWsTile), so each tile's epilogue stores drain under the
-  // next tile's main loop.  PHC_GEMM_WS_GRID=0 keeps one tile per workgroup (A/B aid).
-  static const bool ws_grid = [] {
-    const char *e = getenv("PHC_GEMM_WS_GRID");
-    return PHC_GEMM_WS && !(e && atoi(e) == 0);
-  }();
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  if (ws_grid && d->max_workgroups == 0 && cfg == kCfg256sq && !grad_epi && blocks > cus) blocks = cus;
+  const GemmPlan plan = gemm_plan(d);
+  const int cfg = plan.cfg;
+  const int64_t tiles_m = plan.tiles_m, tiles_n = plan.tiles_n, blocks = plan.blocks;
   GemmArgs g{};
   g.a = static_cast<const char *>(d->a);
   g.b = static_cast<const char *>(d->b);
@@ -1679,7 +1825,7 @@ extern "C" int phc_twin_gemm(const phc_gemm_desc *d, float *bias_grad, void *wor
   // algorithmic FLOPs: the padded depth's zero columns are not counted (k_valid)
   const int kf = d->k_valid > 0 && d->k_valid < d->k ? d->k_valid : d->k;
   if (d->m > kTimedMinRows) g.clk = phc_timer_take(g_gemm_timer, st, blocks, 2.0 * (double)d->m * d->n * kf * d->batch);
-  launch_gemm(d->dtype, d->out_dtype, d->epilogue, cfg, g, blocks, st);
+  launch_gemm(d->dtype, d->out_dtype, d->epilogue, cfg, g, blocks, plan.ws && grad_epi, st);
   if (bias_grad) {
     const int c = d->batch * d->n;
     hipLaunchKernelGGL(k_colsum<>, dim3((unsigned)((c + 63) / 64)), dim3(256), 0, st,
